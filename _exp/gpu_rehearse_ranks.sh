@@ -5,7 +5,7 @@
 O=gpurun_out/${1:-rehearse}; mkdir -p $O
 shift
 for n in "${@:-2}"; do
-  SHADOWTOPO_BENCH_ONE_GPU=1 timeout -k 10 500 python -u bench.py --gpus $n --steps 3 --warmup 1 --no-shim \
+  SHADOWTOPO_BENCH_ONE_GPU=1 timeout -k 10 500 python -u bench.py --full --gpus $n --steps 3 --warmup 1 --no-shim \
     > $O/n$n.json 2> $O/n$n.err || { echo "N=$n failed rc=$?"; tail -30 $O/n$n.err; exit 1; }
   python3 scripts/bench_summary.py $O/n$n.json || true
 done

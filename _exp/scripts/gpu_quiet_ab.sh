@@ -12,7 +12,7 @@ for cfg in ${CFGS:-C3 C4 C5}; do
   for rep in 1 2; do
     for v in ${VARIANTS:-cur base}; do
       if [ $v = cur ]; then unset SHADOWTOPO_EXP_LIB; else export SHADOWTOPO_EXP_LIB=$PWD/_exp/ab/libshadowtopo_$v.so; fi
-      timeout -k 10 400 python -u bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-host-rate > $O/bench_${cfg}_${v}_$rep.json 2> $O/bench_${cfg}_${v}_$rep.err || { echo "bench $cfg $v failed"; tail -20 $O/bench_${cfg}_${v}_$rep.err; exit 1; }
+      timeout -k 10 400 python -u bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-host-rate > $O/bench_${cfg}_${v}_$rep.json 2> $O/bench_${cfg}_${v}_$rep.err || { echo "bench $cfg $v failed"; tail -20 $O/bench_${cfg}_${v}_$rep.err; exit 1; }
       echo -n "$cfg $v $rep: "; python3 -c "import json; d=json.load(open('$O/bench_${cfg}_${v}_$rep.json')); print(d['ms_per_step'], d['engine'].get('host_syncs_per_step'))"
     done
   done

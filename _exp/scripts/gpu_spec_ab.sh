@@ -10,7 +10,7 @@ timeout -k 10 400 python -u -m pytest tests/test_engine_gpu.py -x -q --timeout 1
 rc=$?; tail -2 $O/tests.log; [ $rc -ne 0 ] && { grep -E "FAILED|Error|assert" $O/tests.log | head -20; exit 1; }
 for rep in 1 2; do
   for sp in 0 2; do
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-north-star --no-shim --dense-spec $sp > $O/c2_s${sp}_$rep.json 2> $O/c2_s${sp}_$rep.err || { tail $O/c2_s${sp}_$rep.err; exit 1; }
+    timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-north-star --no-shim --dense-spec $sp > $O/c2_s${sp}_$rep.json 2> $O/c2_s${sp}_$rep.err || { tail $O/c2_s${sp}_$rep.err; exit 1; }
     echo -n "spec $sp rep $rep: "; python3 -c "import json; d=json.load(open('$O/c2_s${sp}_$rep.json')); e=d['engine']; print(round(d['ms_per_step'],4), 'host', round(d['config']['matrix_build_host_ms'],4), 'syncs', e['host_syncs_per_step'], 'rounds', e['rounds_per_step'])"
   done
 done

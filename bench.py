@@ -11,6 +11,13 @@ the rows are exchanged by an RCCL all-gather so every rank holds the full matrix
 is 1000*N vertices.
 
 python bench.py --gpus N --steps K --warmup W        (N>1 via torch.distributed.run)
+
+A plain run sets up, warms up, times exactly K steps and prints the result line; the engine's
+own per-launch timings of those steps (roofline, engine) ride along.  --dump-outputs DIR then
+writes the matrix rows of the last timed step as DIR/{latency,reliability,hops}.npy.  --full adds
+every measurement that takes runs of its own: the host-delivered and fresh-attached-set builds,
+the packed-row probe, the C4 north-star record, the drop-in's host-matrix build, the CPU
+baseline and the rank rehearsal's bit-for-bit check (each with its own --no-... switch).
 """
 from __future__ import annotations
 
@@ -358,6 +365,35 @@ def run_sharded(dist, world, rank, device, A, compute, steps, warmup, chunks=1, 
     return out
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SEED = 20
+
+
+def dump_outputs(ex, out_dir):
+    """--dump-outputs: the latency / reliability / hop rows the last step left in the exchange's
+    buffers (at one rank this rank's rows, at N > 1 the assembled matrix every rank holds), as
+    float64 .npy files.  Past DUMP_BYTES a fixed seeded sample of whole rows, in row order."""
+    import torch
+    A = ex.A
+    total = A if ex.world > 1 else ex.rows
+    k = min(total, max(1, DUMP_BYTES // (24 * max(1, A))))
+    pick = np.arange(total) if k == total else np.sort(
+        np.random.default_rng(DUMP_SEED).choice(total, size=k, replace=False))
+    dev = ex.packs[0].device
+    if ex.world > 1:
+        idx = torch.as_tensor(pick, dtype=torch.int64, device=dev)
+        arrays = [x.index_select(0, idx) for x in ex.full()]
+    else:
+        parts = []
+        for (c0, n), views in zip(ex.bounds, ex.views):
+            idx = torch.as_tensor(pick[(pick >= c0) & (pick < c0 + n)] - c0, dtype=torch.int64, device=dev)
+            parts.append([v.index_select(0, idx) for v in views[:3]])
+        arrays = [torch.cat(p) for p in zip(*parts)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in zip(("latency", "reliability", "hops"), arrays):
+        np.save(os.path.join(out_dir, name + ".npy"), x.cpu().numpy().astype(np.float64))
+
+
 def rehearsal_check(eng, ex, A, device):
     """SHADOWTOPO_BENCH_ONE_GPU rehearsals (every rank on one device): the matrix the exchange
     assembled on this rank against the whole A x A matrix computed by this rank's engine alone,
@@ -607,6 +643,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: host-delivered and fresh-set builds, packed-row probe, C4 north-star "
+                         "record, drop-in host-matrix build, CPU baseline, rank-rehearsal check (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's latency / reliability / hop rows as DIR/<name>.npy (float64; "
+                         "a fixed seeded sample of rows past 64 MB)")
     ap.add_argument("--vertex-loss", action="store_true",
                     help="vertex packetloss on 30 %% of the vertices (synth.with_vertex_loss: C4L for --config C4)")
     ap.add_argument("--no-fresh", action="store_true", help="skip the fresh-attached-set builds (rocprof counter passes "
@@ -757,7 +799,9 @@ def main():
                       hops16=hops16)
     cold_start_ms = cold["ms"]
     elapsed = run["elapsed_s"]
-    check = rehearsal_check(eng, run["exchange"], A, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(run["exchange"], args.dump_outputs)
+    check = rehearsal_check(eng, run["exchange"], A, dev) if args.full else None
     total_sources = A if world > 1 else rows  # every rank's rows per step
     value = total_sources * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
@@ -770,13 +814,13 @@ def main():
     # SURVEY.md 8(d)'s matrix build time "delivered to host": the same steps with the rows
     # landing in page-locked host memory (PCIe included), beside the device-resident figure
     build_host_ms = None
-    if not args.no_host_rate:  # the same condition on every rank: the timing takes barriers
+    if args.full and not args.no_host_rate:  # the same condition on every rank: the timing takes barriers
         build_host_ms = host_build_ms(eng, r0, r1, A, args.steps, run["timed"])
 
     # the build a Shadow run pays once per attach epoch: a new attached set (same size, seed
     # 13) before every timed build, so the set-dependent work is inside the timed region
     fresh_ms = fresh_prep_ms = None
-    if not args.no_fresh:
+    if args.full and not args.no_fresh:
         other = np.sort(np.random.default_rng(13).choice(g.n, size=A, replace=False)).astype(np.int32)
         fresh_ms, fresh_prep_ms = fresh_build_ms(eng, [g.attached, other], r0, r1, args.steps, run["timed"], dev)
     sharding = sharded_report(dist, world, run, args.steps, st["relax_ms"] / args.steps, rows)
@@ -787,7 +831,7 @@ def main():
     # counts: the topology API never returns them); the copy of a batch group overlaps the
     # next group's computation.  Also the same rows into ordinary pageable numpy arrays.
     host_ms = host_pageable_ms = None
-    if rank == 0 and world == 1 and rows > 0 and not args.no_host_rate:
+    if args.full and rank == 0 and world == 1 and rows > 0 and not args.no_host_rate:
         outs = [E.pinned_empty((rows, A), np.float64), E.pinned_empty((rows, A), np.float64), None,
                 E.pinned_empty((rows, A), np.uint8)]
         eng.compute_rows_into(r0, r1, *outs)  # first touch of the buffers
@@ -809,7 +853,7 @@ def main():
         exchange.update(gathered_bytes_per_step=run["allgather_bytes"],
                         raw_bytes_per_step=sum(p.numel() for p in run["exchange"].packs) * world,
                         exchange_ms=run["allgather_s"] / args.steps * 1e3)
-    elif dense and rows > 0 and args.exchange == "packed":
+    elif args.full and dense and rows > 0 and args.exchange == "packed":
         ex = run["exchange"]
         lat_v, rel_v, hops_v = ex.views[0]
         n0 = min(rows, ex.bounds[0][1])
@@ -821,7 +865,7 @@ def main():
     # the north-star record (C4 sharded over every rank + all-gather) at every GPU count: all
     # ranks take part (barriers, all-gather), rank 0 reports
     north = None
-    if args.config == "C2" and args.scale == 1.0 and not args.no_north_star:
+    if args.full and args.config == "C2" and args.scale == 1.0 and not args.no_north_star:
         eng.close()
         eng = None
         try:
@@ -836,7 +880,7 @@ def main():
     # shim's page-locked host matrix): rank 0 drives every GPU of the node while the other
     # ranks wait at the barrier
     shim = None
-    if args.config == "C2" and args.scale == 1.0 and not args.no_north_star and not args.no_shim:
+    if args.full and args.config == "C2" and args.scale == 1.0 and not args.no_north_star and not args.no_shim:
         if rank == 0:
             try:
                 shim = shim_host_matrix(world)
@@ -846,7 +890,7 @@ def main():
             dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             share = int(os.environ.get("OMP_NUM_THREADS", "0")) or len(os.sched_getaffinity(0))
             cpu = cpu_baseline(g, args.cpu_sources, all_cores=share)
