@@ -158,7 +158,8 @@ typedef struct shadowtopo_engine shadowtopo_engine;
                                               group's copy behind the next group's rounds; 0 (default) = automatic (one
                                               group unless the rows outweigh the rounds). Results are identical. */
 #define SHADOWTOPO_OPT_SWEEP_STATS 37       /* diagnostics: 1 = after each pruned two-part sweep, the chunks its blocks staged
-                                              are summed into stats.sweep_chunks (one host synchronisation per sweep;
+                                              are summed into stats.sweep_chunks (heavy-first order on) and the rows its chunk
+                                              loops logged into stats.sweep_hit_rows (one host synchronisation per sweep;
                                               0 = off, the default) */
 #define SHADOWTOPO_OPT_SWEEP_WINDOWS 38     /* pruned dense sweep: the chunk windows whose skip masks are evaluated at once:
                                               bits 0-7 = the neighbour window after the tile's own chunk (default 8,
@@ -172,6 +173,13 @@ typedef struct shadowtopo_engine shadowtopo_engine;
 #define SHADOWTOPO_OPT_SWEEP_WAVES 41       /* pruned dense sweep: the chunk loop's blocks are 4 waves x 8 destinations
                                               (4, the default) or 8 waves x 8 (8: one staged chunk serves 64 columns).
                                               Results are identical. */
+#define SHADOWTOPO_OPT_SWEEP_LANES 44       /* pruned dense sweep in parts: the chunk loop's lanes are the batch's 64 sources
+                                              (0: a wave tests 64 sources x 8 destinations) or 64 consecutive destinations
+                                              (1, the default: 8 sources x 64 destinations, fewer live chunks per wave;
+                                              C2 step 2.99 -> 2.71 ms). 1 applies to the
+                                              plain 4-wave f32 loop only (OPT_SWEEP_GLDS, OPT_SWEEP_WAVES 8,
+                                              OPT_SWEEP_REFILTER and OPT_DENSE_W16 off); otherwise the source-lane loop
+                                              runs. Results are identical. */
 #define SHADOWTOPO_OPT_SEED_SKIP 42         /* dense round 0: the exact pass leaves a pair whose seed candidate (the source's
                                               own arc) won untainted unread and unwritten -- the stored state is the seed's
                                               (1, the default) -- or re-reads and compares it (0). Results are identical. */

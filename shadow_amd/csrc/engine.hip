@@ -1903,6 +1903,291 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(TB == 1
     }
 }
 
+// The pruned chunk loop with destination lanes (OPT_SWEEP_LANES 1): k_relax_dense_f<.., PR, PH = 1>'s
+// filter with the roles of D32 and W32 swapped.  The filter D32(u, s) + W32(u, t) <= thr(t, s) is
+// symmetric in its two operands, so either may be the per-lane one.
+//  * block = one batch, one half h of its sources (32 h .. 32 h + 31) and one tile of 64 consecutive
+//    destinations t0 .. t0 + 63 of the locality order; wave w owns the source octet s0 = 32 h + 8 w,
+//    lane = destination t0 + lane.  A wave's 8 x 64 pairs are two small blobs of the embedding (64
+//    consecutive destinations are almost a point, 8 consecutive sources of the 64-source batch a small
+//    patch) instead of a point and the batch's whole patch, so fewer chunks lie near any of its pairs;
+//  * thr[j] (per lane, j = source of the octet) starts as the source-lane loop's thr[t] for the same
+//    pair: f32_thr(min(current distance, seed candidate)), NaN for a lane past V or a slot without a
+//    source;
+//  * per chunk the block stages W32p[u0 + r][t0 .. t0 + 63] (the per-lane operand: 8 KB, no perm
+//    lookup) and D32[perm[u0 + r]][32 h .. 32 h + 31] (wave-uniform: 4 KB), double-buffered in the
+//    source-lane loop's 24 KB;
+//  * per row: w = one LDS word per lane, the octet's 8 distances two broadcast 16-byte reads, a lane
+//    passes iff w <= max_j fl32(thr[j] - d_j).  A NaN d_j (unreached, or the source's own row) drops
+//    out of the maximum, a NaN w (no arc) fails the compare.  On a wave vote every lane tightens
+//    every thr[j] at once to bits(fl32(d_j + w)) + 9, as the source-lane loop does;
+//  * chunk skip and windows: minD[b][c][s0 .. s0 + 7] is wave-uniform, minW[c][t0 + lane] per lane:
+//    a lane can pass no row of chunk c unless minW <= max_j fl32(thr[j] - minD_j) (rounding is
+//    monotone, d_j >= minD_j, w >= minW);
+//  * hit log in the source-lane loop's format, so k_relax_dense_f<.., PH = 2> reads it unchanged:
+//    word ((b * Vp / 8) + destination octet) * nchunks + c, bit r.  A lane collects its passes of the
+//    chunk, each group of 8 lanes ORs them and does one atomicOr: the 8 waves of a tile's two blocks
+//    share each word, so the launch clears the log first and dead chunks are not written at all.
+// Why the log stays exact: a pair's thr only falls to f32 upper bounds of candidates that the exact
+// pass will see or that some row really offers, so thr(t, s) >= f32_thr(final bc(t, s)) at every
+// moment, whatever order the other pairs' thresholds fall in.  Every row whose exact candidate meets
+// or beats a pair's final key therefore passes that pair's lane when it is tested and is logged (a
+// skipped chunk holds no such row, by the bound above); the exact pass decides everything else.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_sweep_dest_lanes(
+    const float* __restrict__ W32p, const double* __restrict__ Wp, int32_t Vp, Pools pools, int32_t V, int32_t nb,
+    int32_t ntl, int32_t thresh, const int32_t* __restrict__ cnt_prev, uint32_t* __restrict__ hitlog,
+    const int32_t* __restrict__ perm, const float* __restrict__ minW, const float* __restrict__ minD,
+    const int32_t* __restrict__ ipos, int32_t spiral, int32_t win1, const int32_t* __restrict__ border,
+    uint32_t* __restrict__ bweight) {
+    constexpr int NT = 256, SO = 8;  // threads per block; sources per wave
+    constexpr int BS = 32, BD = 64;  // block: sources x destinations
+    struct SweepLds {
+        float d[2][SRS * BS];
+        float w[2][SRS * BD];
+        unsigned long long win[2];
+    };
+    __shared__ __attribute__((aligned(16))) SweepLds slds;
+    auto& sD = slds.d;
+    auto& sW = slds.w;
+    auto& sWin = slds.win;
+    const int64_t Lb = border ? (int64_t)border[blockIdx.x] : (int64_t)blockIdx.x;
+    int32_t b, it;
+    if (!xcd_tile(Lb, nb, 2 * ntl, b, it)) return;  // block-uniform exits only (barriers below)
+    const int32_t h = it & 1, t0 = (it >> 1) * BD;
+    if (!(cnt_prev[b] > thresh) || t0 >= V) {
+        if (bweight && threadIdx.x == 0) bweight[Lb] = 0u;
+        return;
+    }
+    const int32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int32_t s0 = BS * h + SO * wave;
+    const int32_t p = t0 + lane;  // this lane's destination (position in the locality order; < Vp)
+    const BatchDev B = batch_view(pools, b);
+    float thr[SO];
+    {
+        const int32_t v = perm[p];
+        double cd[SO];
+#pragma unroll
+        for (int j = 0; j < SO; ++j) cd[j] = B.D[(size_t)v * KL + s0 + j];  // padding rows are +inf
+#pragma unroll
+        for (int j = 0; j < SO; ++j) {
+            const int32_t sj = B.srcv[s0 + j];
+            const double ws = (sj >= 0 && sj != v) ? Wp[(size_t)ipos[sj >= 0 ? sj : 0] * Vp + p] : dinf();
+            const double bc = ws < dinf() ? 0.0 + ws : dmax();
+            thr[j] = sj >= 0 && p < V ? f32_thr(cd[j] < bc ? cd[j] : bc) : __int_as_float(0x7fc00000);
+        }
+    }
+    const int32_t nrows = (V + SRS - 1) / SRS * SRS;  // <= Vp: rows past V are NaN padding
+    const int32_t nchunks = nrows / SRS;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) const f4 gf4;
+    constexpr int WQ = BD / 4;               // float4 per W32p chunk row
+    constexpr int DQ4 = BS / 4;              // float4 per D32 chunk row
+    constexpr int WQT = SRS * WQ / NT;       // float4 of W32p per thread
+    static_assert(SRS * DQ4 == NT && WQT * NT == SRS * WQ, "one D32 piece and whole W32p pieces per thread");
+    f4 pd, pw[WQT];
+    float mdn[SO], mdc[SO], mwn, mwc;  // the chunk's skip bounds: min D32 per source (wave-uniform), min W32 per lane
+    const gfloat* mDb = (const gfloat*)minD + (size_t)b * nchunks * KL + s0;
+    const gfloat* mWl = (const gfloat*)minW + p;
+    const int32_t c0 = (int32_t)((int64_t)t0 / SRS % nchunks);  // the chunk holding the tile's first row
+    const int32_t sL = c0, sR = nchunks - 1 - c0, sM = sL < sR ? sL : sR;
+    auto chunk_of = [&](int32_t j) {  // k_relax_dense_f's chunk order
+        if (!spiral) return (c0 + j) % nchunks;
+        if (j <= 2 * sM) return j == 0 ? c0 : ((j & 1) ? c0 + (j + 1) / 2 : c0 - j / 2);
+        return sR > sL ? c0 + j - sM : c0 - (j - sM);
+    };
+    // the vertex of this thread's D32 row of the chunk of order index j, loaded one chunk ahead of
+    // the fetch that uses it
+    auto perm_of = [&](int32_t j) { return perm[chunk_of(j) * SRS + (int)threadIdx.x / DQ4]; };
+    auto fetch = [&](int32_t j, int32_t prow) {
+        const int32_t c = chunk_of(j);
+        const int32_t u0 = c * SRS;
+        pd = *(gf4*)(B.D32 + (size_t)prow * KL + BS * h + ((int)threadIdx.x % DQ4) * 4);
+#pragma unroll
+        for (int j2 = 0; j2 < SO; ++j2) mdn[j2] = mDb[(size_t)c * KL + j2];
+        mwn = mWl[(size_t)c * Vp];
+#pragma unroll
+        for (int i = 0; i < WQT; ++i) {
+            const int e = threadIdx.x + i * NT;
+            pw[i] = *(gf4*)((const gfloat*)W32p + (size_t)(u0 + e / WQ) * Vp + t0 + (e % WQ) * 4);
+        }
+    };
+    auto stash = [&](int buf) {
+        *(f4*)&sD[buf][threadIdx.x * 4] = pd;
+#pragma unroll
+        for (int i = 0; i < WQT; ++i) *(f4*)&sW[buf][(threadIdx.x + i * NT) * 4] = pw[i];
+    };
+    auto advance = [&]() {
+#pragma unroll
+        for (int j = 0; j < SO; ++j) mdc[j] = mdn[j];
+        mwc = mwn;
+    };
+    // block-wide chunk skipping over windows of chunks, as in k_relax_dense_f
+    if (threadIdx.x == 0) sWin[0] = sWin[1] = 0ull;
+    __syncthreads();
+    int32_t cur_win = -1;
+    unsigned long long cur_live = 0ull;
+    const int32_t w1 = (win1 & 0xff) < 64 ? (win1 & 0xff) : 0;
+    const int32_t wf = ((win1 >> 8) & 0xff) > 0 && ((win1 >> 8) & 0xff) < 64 ? (win1 >> 8) & 0xff : 64;
+    auto win_of = [&](int32_t j) {
+        if (j == 0) return 0;
+        if (w1) return j <= w1 ? 1 : 2 + (j - 1 - w1) / wf;
+        return 1 + (j - 1) / wf;
+    };
+    auto win_base = [&](int32_t wi) {
+        if (wi == 0) return 0;
+        if (w1) return wi == 1 ? 1 : 1 + w1 + (wi - 2) * wf;
+        return 1 + (wi - 1) * wf;
+    };
+    auto win_size = [&](int32_t wi) { return wi == 0 ? 1 : (w1 && wi == 1 ? w1 : wf); };
+    constexpr int WG = 4;  // chunks whose bounds are in flight at once (WG x SO SGPRs of minD)
+    auto eval_window = [&](int32_t wi) -> unsigned long long {
+        const int32_t base = win_base(wi);
+        const int32_t nw = nchunks - base < win_size(wi) ? nchunks - base : win_size(wi);
+        unsigned long long wm = 0ull;
+        const int32_t cl = chunk_of(base + (lane < nw ? lane : 0));  // lane i's chunk of the window
+        for (int32_t j0 = 0; j0 < nw; j0 += WG) {
+            float md[WG][SO], mw[WG];
+#pragma unroll
+            for (int jj = 0; jj < WG; ++jj) {
+                const int32_t c = __builtin_amdgcn_readlane(cl, j0 + jj < nw ? j0 + jj : 0);
+#pragma unroll
+                for (int j = 0; j < SO; ++j) md[jj][j] = mDb[(size_t)c * KL + j];
+                mw[jj] = mWl[(size_t)c * Vp];
+            }
+#pragma unroll
+            for (int jj = 0; jj < WG; ++jj) {
+                float tm = thr[0] - md[jj][0];
+#pragma unroll
+                for (int j = 1; j < SO; ++j) tm = fmaxf(tm, thr[j] - md[jj][j]);
+                if (__ballot(mw[jj] <= tm) && j0 + jj < nw) wm |= 1ull << (j0 + jj);
+            }
+        }
+        if (threadIdx.x == 0) sWin[(wi + 1) & 1] = 0ull;  // the next window's slot: nobody ORs into it before this barrier
+        if (lane == 0 && wm) atomicOr(&sWin[wi & 1], wm);
+        __syncthreads();
+        return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sWin[wi & 1] >> 32)) << 32) |
+               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sWin[wi & 1]);
+    };
+    auto next_live = [&](int32_t from) -> int32_t {
+        while (from < nchunks) {
+            const int32_t wi = win_of(from);
+            if (wi != cur_win) {
+                cur_win = wi;
+                cur_live = eval_window(wi);
+            }
+            const unsigned long long m = cur_live & (~0ull << (from - win_base(wi)));
+            if (m) return win_base(wi) + __builtin_ctzll(m);
+            from = win_base(wi + 1);
+        }
+        return -1;
+    };
+    // this lane's destination octet's log words, one per chunk
+    uint32_t* hl = hitlog + ((size_t)b * (size_t)(Vp / 8) + (size_t)(p / 8)) * nchunks;
+    int32_t prow_n = 0;
+    uint32_t nvis = 0;  // chunks this block staged (its weight for the next sweep's order)
+    int32_t itc = next_live(0);
+    if (itc >= 0) {
+        prow_n = perm_of(itc);
+        fetch(itc, prow_n);
+        stash(0);
+        advance();
+    }
+    int32_t itn = itc >= 0 ? next_live(itc + 1) : -1;
+    if (itn >= 0) prow_n = perm_of(itn);
+    __syncthreads();
+    int bufc = 0;
+    while (itc >= 0) {
+        const int32_t c = chunk_of(itc);
+        const int cur = bufc;
+        const bool more = itn >= 0;
+        if (more) fetch(itn, prow_n);
+        const int32_t itn2 = more ? next_live(itn + 1) : -1;  // block-uniform (a window evaluation holds a barrier)
+        if (itn2 >= 0) prow_n = perm_of(itn2);
+        bool run;
+        {
+            float tm = thr[0] - mdc[0];
+#pragma unroll
+            for (int j = 1; j < SO; ++j) tm = fmaxf(tm, thr[j] - mdc[j]);
+            run = __ballot(mwc <= tm) != 0;
+        }
+        uint32_t hits = 0;  // bit r: this lane passed row u0 + r
+        typedef __attribute__((address_space(3))) const f4 lf4;
+        typedef __attribute__((address_space(3))) const float lf1;
+        // the slabs' row bases in VGPRs kept live across the chunk (rows are immediate offsets)
+        uint32_t wbase = (uint32_t)(uintptr_t)(lf1*)&sW[cur][lane];
+        uint32_t dbase = (uint32_t)(uintptr_t)(lf4*)&sD[cur][SO * wave];
+        asm volatile("" : "+v"(wbase), "+v"(dbase));
+        float wn;
+        f4 dn[SO / 4];
+        auto lds_row = [&](int r) {  // issued one row ahead of its use
+            wn = *(lf1*)(uintptr_t)(wbase + (uint32_t)(r * BD) * 4u);
+#pragma unroll
+            for (int j = 0; j < SO / 4; ++j) dn[j] = *(lf4*)(uintptr_t)(dbase + (uint32_t)(r * BS + 4 * j) * 4u);
+        };
+        if (run) lds_row(0);
+#pragma unroll 8
+        for (int r = 0; r < (run ? SRS : 0); ++r) {
+            const float w = wn;
+            f4 d4[SO / 4];
+#pragma unroll
+            for (int j = 0; j < SO / 4; ++j) d4[j] = dn[j];
+            if (r + 1 < SRS) lds_row(r + 1);
+            // slacks thr_j - d_j two at a time (v_pk_add_f32), their max as a chain of v_max3
+            typedef float f2 __attribute__((ext_vector_type(2)));
+            float x[SO];
+#pragma unroll
+            for (int j = 0; j < SO / 4; ++j) {
+                const f2 a = f2{thr[4 * j], thr[4 * j + 1]} - f2{d4[j].x, d4[j].y};
+                const f2 e = f2{thr[4 * j + 2], thr[4 * j + 3]} - f2{d4[j].z, d4[j].w};
+                x[4 * j] = a.x;
+                x[4 * j + 1] = a.y;
+                x[4 * j + 2] = e.x;
+                x[4 * j + 3] = e.y;
+            }
+            float g = fmaxf(fmaxf(x[0], x[1]), x[2]);
+#pragma unroll
+            for (int t = 3; t + 1 < SO; t += 2) g = fmaxf(fmaxf(g, x[t]), x[t + 1]);
+            g = fmaxf(g, x[SO - 1]);
+            const bool pass = w <= g;
+            if (__ballot(pass)) {
+                hits |= pass ? 1u << r : 0u;
+                // every lane may lower thr_j to bits(c32) + 9 (k_relax_dense_f): an infinite or NaN
+                // candidate, or a bound that would wrap past +inf, leaves thr as it is
+#pragma unroll
+                for (int j = 0; j < SO / 4; ++j) {
+                    const float dj[4] = {d4[j].x, d4[j].y, d4[j].z, d4[j].w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float c32 = dj[i] + w;
+                        const float nbd = __int_as_float(__float_as_int(c32) + 9);
+                        float& th = thr[4 * j + i];
+                        th = ((c32 < __int_as_float(0x7f800000)) & (nbd < th)) ? nbd : th;
+                    }
+                }
+            }
+        }
+        if (__ballot(hits != 0u)) {
+            // OR over each group of 8 lanes (one destination octet = one log word)
+            uint32_t h8 = hits;
+            h8 |= (uint32_t)__shfl_xor((int)h8, 1);
+            h8 |= (uint32_t)__shfl_xor((int)h8, 2);
+            h8 |= (uint32_t)__shfl_xor((int)h8, 4);
+            if ((lane & 7) == 0 && h8) atomicOr(hl + c, h8);
+        }
+        if (more) {
+            stash(cur ^ 1);
+            advance();
+        }
+        __syncthreads();
+        bufc ^= 1;
+        itc = itn;
+        itn = itn2;
+        ++nvis;
+    }
+    if (bweight && threadIdx.x == 0) bweight[Lb] = nvis;
+}
+
 // Heavy-first order of a pruned chunk-loop launch (border for k_relax_dense_f<.., PH = 1>):
 // block (x, part) sorts the S = nblocks / 8 items XCD x runs in that part (L = 8 j + x, j < S)
 // by the chunk counts their blocks staged last time, largest first (ties by j), and writes
@@ -3664,6 +3949,7 @@ struct shadowtopo_engine {
     int32_t opt_sweep_stats = 0;      // diagnostics: staged chunks of the pruned sweeps (OPT_SWEEP_STATS)
     unsigned long long* d_sweep_hits = nullptr;  // OPT_SWEEP_STATS: the exact passes' logged rows
     int32_t opt_sweep_waves = 4;      // pruned sweep chunk loop: waves per block, 4 or 8 (OPT_SWEEP_WAVES)
+    int32_t opt_sweep_lanes = 1;      // pruned sweep chunk loop: lanes = sources (0) or destinations (1) (OPT_SWEEP_LANES)
     int32_t opt_sweep_refilter = 0;   // exact pass re-tests logged rows against the final thresholds (OPT_SWEEP_REFILTER)
     int32_t opt_seed_skip = 1;        // round-0 exact pass leaves untainted seed winners unread (OPT_SEED_SKIP)
     int32_t opt_delta_w16 = 1;        // pruned delta rounds filter with fp16 slabs (OPT_DELTA_W16)
@@ -4040,6 +4326,19 @@ hipError_t launch_dense_ft(shadowtopo_engine* eng, int32_t nbg, int32_t par, int
                     // to NaN (no changed pair) first
                     if (e == hipSuccess && mdc_out)
                         e = hipMemsetD32Async((hipDeviceptr_t)mdc_out, 0x7fc00000, (size_t)nbg * (eng->Vp / KL) * KL, s);
+                    // (the diagnostics' counter is cleared ahead of the fork: every part's exact pass adds to it)
+                    if (e == hipSuccess && eng->opt_sweep_stats && !eng->d_sweep_hits)
+                        e = hipMalloc((void**)&eng->d_sweep_hits, 2 * sizeof(unsigned long long));
+                    if (e == hipSuccess && eng->opt_sweep_stats)
+                        e = hipMemsetAsync(eng->d_sweep_hits, 0, 2 * sizeof(unsigned long long), s);
+                    // destination lanes (OPT_SWEEP_LANES 1, k_sweep_dest_lanes): the plain 4-wave f32 loop only
+                    const bool dest_lanes = eng->opt_sweep_lanes && eng->opt_sweep_waves != 8 && !eng->opt_sweep_glds &&
+                                            !eng->opt_sweep_refilter;
+                    // nobody owns a word of its hit log (the 8 waves of a tile's two blocks OR into it), so
+                    // the log is cleared first: all parts' slices ahead of the fork (a part's own clear on its
+                    // own stream queued behind the other part's chunk loop and started its loop 0.4 ms late)
+                    if (e == hipSuccess && dest_lanes)
+                        e = hipMemsetAsync(eng->d_hitlog, 0, (size_t)nbg * (size_t)(eng->Vp / TDT) * nchunks * sizeof(uint32_t), s);
                     if (e == hipSuccess) e = hipEventRecord(eng->ev_h0, s);
                     for (int k = 0; k < parts - 1 && e == hipSuccess; ++k) e = hipStreamWaitEvent(eng->aux_stream[k], eng->ev_h0, 0);
                     if (e != hipSuccess) return e;
@@ -4047,11 +4346,6 @@ hipError_t launch_dense_ft(shadowtopo_engine* eng, int32_t nbg, int32_t par, int
                     // buffer `cur` (sorted after the previous sweep of the same shape), the
                     // blocks record their chunk counts, and the sort for the next sweep writes
                     // buffer cur ^ 1 (no running sweep reads it)
-                    if (eng->opt_sweep_stats && !eng->d_sweep_hits &&
-                        (e = hipMalloc((void**)&eng->d_sweep_hits, 2 * sizeof(unsigned long long))) != hipSuccess)
-                        return e;
-                    if (eng->opt_sweep_stats && (e = hipMemsetAsync(eng->d_sweep_hits, 0, 2 * sizeof(unsigned long long), s)) != hipSuccess)
-                        return e;
                     if (eng->opt_sweep_refilter) {
                         const size_t need_t = (size_t)nbg * eng->Vp * KL;
                         if (eng->thrio_n < need_t) {
@@ -4063,6 +4357,7 @@ hipError_t launch_dense_ft(shadowtopo_engine* eng, int32_t nbg, int32_t par, int
                         }
                     }
                     const int cur = eng->heavy_buf;
+                    const int32_t ntl = (eng->V + KL - 1) / KL;  // destination-lane tiles
                     HeavyArgs ha{};
                     bool sort_any = false;
                     auto part = [&](hipStream_t st, int32_t b0, int32_t n, int k) {
@@ -4074,9 +4369,14 @@ hipError_t launch_dense_ft(shadowtopo_engine* eng, int32_t nbg, int32_t par, int
                         // 8 waves x 8: 64 destinations per block, one staged D32 chunk for twice
                         // the columns; the exact pass keeps 4-wave blocks (hit logs are per wave tile)
                         const bool w8 = eng->opt_sweep_waves == 8;
-                        const int32_t ntb1 = w8 ? (eng->V + 8 * TDT - 1) / (8 * TDT) : ntb;
+                        // destination lanes: blocks of 32 sources x 64 destinations, two per 64-destination tile
+                        const bool dl = dest_lanes;
+                        const int32_t ntb1 = dl ? 2 * ntl : w8 ? (eng->V + 8 * TDT - 1) / (8 * TDT) : ntb;
                         const int64_t nbl1 = 8 * (((int64_t)n * ntb1 + 7) / 8);
-                        const int64_t key = ((int64_t)b0 << 42) | ((int64_t)n << 21) | ((int64_t)w8 << 20) | ntb1;
+                        // (the shape is part of the key: an order sorted for one shape's items is never
+                        // read by the other's blocks)
+                        const int64_t key = ((int64_t)b0 << 42) | ((int64_t)n << 21) | ((int64_t)w8 << 20) |
+                                            ((int64_t)dl << 19) | ntb1;
                         bool heavy = eng->opt_heavy_first && k < 4 && nbl1 / 8 <= HEAVY_MAX;
                         if (heavy && eng->heavy_cap[k] < (size_t)nbl1) {
                             for (void* q : {(void*)eng->d_bweight[k], (void*)eng->d_border[k][0], (void*)eng->d_border[k][1]})
@@ -4097,7 +4397,12 @@ hipError_t launch_dense_ft(shadowtopo_engine* eng, int32_t nbg, int32_t par, int
                         }
                         const int32_t* ord = heavy && eng->heavy_key[k] == key ? eng->d_border[k][cur] : nullptr;
                         float* tio = eng->opt_sweep_refilter ? eng->d_thrio + (size_t)b0 * eng->Vp * KL : nullptr;
-                        if (w8 && eng->opt_sweep_glds)
+                        if (dl)
+                            hipLaunchKernelGGL(k_sweep_dest_lanes, dim3((uint32_t)nbl1), dim3(256), 0, st, eng->d_W32p,
+                                               eng->d_Wp, eng->Vp, P, eng->V, n, ntl, thresh, cnt_prev + b0, hl,
+                                               eng->d_perm, eng->d_minW, mD, eng->d_pos, eng->opt_sweep_spiral,
+                                               eng->opt_sweep_win1, ord, heavy ? eng->d_bweight[k] : nullptr);
+                        else if (w8 && eng->opt_sweep_glds)
                             hipLaunchKernelGGL((k_relax_dense_f<TDT, XR, 1, true, 1, 8, false, true>), dim3((uint32_t)nbl1),
                                                dim3(512), 0, st, eng->d_W32p, eng->d_Wp, eng->d_WI, eng->Vp, eng->g.in_r,
                                                P, eng->V, n, ntb1, par, thresh, cnt_prev + b0, cnt_cur + b0, nullptr, hl,
@@ -4165,15 +4470,15 @@ hipError_t launch_dense_ft(shadowtopo_engine* eng, int32_t nbg, int32_t par, int
                         if (e == hipSuccess) e = hipStreamWaitEvent(s, eng->ev_hp[k], 0);
                     }
                     if (e != hipSuccess) return e;
-                    if (eng->opt_sweep_stats && sort_any) {  // diagnostics: the chunks this sweep staged
+                    if (eng->opt_sweep_stats) {  // diagnostics: the chunks this sweep staged, the rows it logged
                         if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-                        for (int k = 0; k < parts && k < 4; ++k) {
+                        for (int k = 0; k < parts && k < 4 && sort_any; ++k) {
                             if (!ha.w[k]) continue;
                             std::vector<uint32_t> wk((size_t)ha.slots[k] * 8);
                             if ((e = hipMemcpy(wk.data(), ha.w[k], wk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess)
                                 return e;
                             for (uint32_t x : wk) eng->st.sweep_chunks += x;
-                            const int32_t ntbs = eng->opt_sweep_waves == 8 ? (eng->V + 8 * TDT - 1) / (8 * TDT) : ntb;
+                            const int32_t ntbs = dest_lanes ? 2 * ntl : eng->opt_sweep_waves == 8 ? (eng->V + 8 * TDT - 1) / (8 * TDT) : ntb;
                             eng->st.sweep_chunk_slots += (int64_t)(bound(k + 1) - bound(k)) * ntbs * (int64_t)nchunks;
                         }
                         unsigned long long hits = 0;
@@ -6565,6 +6870,10 @@ int shadowtopo_set_option(shadowtopo_engine* eng, int32_t key, int64_t value) {
         case SHADOWTOPO_OPT_SWEEP_REFILTER:
             if (value != 0 && value != 1) return fail(SHADOWTOPO_EINVAL, "sweep refilter must be 0 or 1");
             eng->opt_sweep_refilter = (int32_t)value;
+            return SHADOWTOPO_OK;
+        case SHADOWTOPO_OPT_SWEEP_LANES:
+            if (value != 0 && value != 1) return fail(SHADOWTOPO_EINVAL, "sweep lanes must be 0 or 1");
+            eng->opt_sweep_lanes = (int32_t)value;
             return SHADOWTOPO_OK;
         case SHADOWTOPO_OPT_SWEEP_STATS:
             eng->opt_sweep_stats = value ? 1 : 0;
